@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — spectral-mix tokens/s at (B=256, N=4096, D=768) per GPU, batch-sharded over N GPUs.
 
-    python bench.py [--gpus N --steps K --warmup W] [--io f32|bf16] [--shape B,N,D] [--groups G]
+    python bench.py [--gpus N --steps K --warmup W] [--io f32|bf16] [--shape B,N,D] [--groups G] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,15 +10,21 @@ synthetic batch already resident in HBM.  Weak scaling: every rank owns B=256 ba
 configuration is BASELINE.json's B=2048 batch shard); there is no collective in the data path, only the
 barrier + MAX-over-ranks timing reduction the contract asks for.
 
+A plain run sets up, warms up, times the K steps and prints the line; nothing else runs on the GPU.  `--full` adds the
+informational measurements (cold_start, the copy-probe ceilings in `roofline`, `variants`, live `roofline.traffic`,
+`cpu_baseline`), each in the same process after the timed region.  `--dump-outputs DIR` writes what the last timed step
+computed (`dump_outputs`).
+
 Prints ONE JSON line on rank 0 with
   value        whole-job tokens/s = B_total * N * K / (last rank's finish - first rank's start) of the K timed steps: every rank
                stamps the node's monotonic clock behind the opening barrier + synchronize and behind its closing synchronize (in front
                of the closing barrier), so the job time is MAX over ranks of the end minus MIN over ranks of the start — the
                max-over-ranks wall time without the latency of the closing barrier itself (`timing` in the line says so;
                `wall_incl_closing_barrier_s` is the older definition)
+  ms_per_step  the same job time / K, in milliseconds
   roofline     dominant kernel vs the HBM roofline: algorithmic bytes per launch / average launch duration,
                the duration measured live with HIP events on the launch stream over the timed region
-  cpu_baseline the oracle's torch.fft restatement of the same statements timed on this box's host cores
+  cpu_baseline (--full) the oracle's torch.fft restatement of the same statements timed on this box's host cores
                on a bounded sample (rank 0, single-GPU runs only)
 """
 from __future__ import annotations
@@ -171,11 +177,57 @@ def live_traffic(a, timeout_s=150.0):
             "seconds": time.perf_counter() - t0}, "ok"
 
 
+DUMP_BUDGET_BYTES = 48 << 20     # all ranks together (the dump may hold at most 64 MB)
+DUMP_MAX_ELEMENTS = 4 << 20
+DUMP_SEED = 0
+
+
+def dump_outputs(path, out, rank, world):
+    """`--dump-outputs DIR`: the output tensor of the last timed step, as a caller of spectral_mix receives it, in float32 .npy files
+    (`out` for rank 0, `out_rank<r>` for the others).  The whole tensor when it fits DUMP_BUDGET_BYTES / world; otherwise a fixed sample
+    drawn with numpy's PCG64 seeded with DUMP_SEED: `<name>_batches.npy` = the whole (N, D) slices of the batch elements
+    rng.choice(B, k, replace=False) (sorted), then `<name>_elements.npy` = the elements at the flat indices rng.integers(0, numel, m)
+    (sorted).  Same arguments -> same inputs, same indices: two builds compare output for output.  Returns a record for the line."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    name = "out" if rank == 0 else f"out_rank{rank}"
+    budget = DUMP_BUDGET_BYTES // max(1, world)
+    B, numel = out.shape[0], out.numel()
+    slice_bytes = (numel // B) * 4
+    files = {}
+
+    def save(fname, t):
+        arr = t.detach().float().cpu().numpy()
+        np.save(os.path.join(path, fname + ".npy"), arr)
+        files[fname] = list(arr.shape)
+
+    if numel * 4 <= budget:
+        save(name, out)
+        return {"dir": path, "files": files, "sample": "whole tensor"}
+    rng = np.random.default_rng(DUMP_SEED)
+    k = min(B, (budget // 2) // slice_bytes)
+    if k > 0:
+        bidx = np.sort(rng.choice(B, size=k, replace=False))
+        save(name + "_batches", out[torch.from_numpy(bidx).to(out.device)])
+    m = min(DUMP_MAX_ELEMENTS, (budget - k * slice_bytes) // 4)
+    eidx = np.sort(rng.integers(0, numel, size=m, dtype=np.int64))
+    save(name + "_elements", out.reshape(-1)[torch.from_numpy(eidx).to(out.device)])
+    return {"dir": path, "files": files,
+            "sample": f"numpy default_rng({DUMP_SEED}): {k} batch elements by choice(B, {k}, replace=False), then {m} flat indices by "
+                      f"integers(0, numel, {m}), both sorted"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the informational measurements: cold start, copy-probe ceilings, other storage "
+                         "dtypes / sizes / allocations, backward, wavelet refinement, live rocprofv3 traffic, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step to DIR/*.npy (float32; a fixed seeded sample when it is large)")
     ap.add_argument("--no-placement-probe", action="store_true", help="skip the informational best-of-4-allocations variant")
     ap.add_argument("--prewarm", type=int, default=60,
                     help="untimed launches BEFORE the --warmup steps: the chip needs ~25 back-to-back launches (40 ms) to leave its idle "
@@ -190,6 +242,8 @@ def main():
                                                           "the line then replays profiles/pmc_latest.json and says so")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.pmc_child:
         pmc_child(a)
         return
@@ -251,12 +305,12 @@ def main():
         torch.cuda.synchronize()
 
     # The contract's protocol WITHOUT the power-state prewarm, from the idle state the process starts in (the protocol of rounds 1-2, ADVICE
-    # r03): W warm-up + K timed steps.  Informational (`cold_start`): round-over-round comparisons must use like for like.  Every world
-    # size runs it (rank 0 reports its own), and its launches COUNT as prewarm launches, so that the number of launches in front of the
-    # timed region is the same for every N and every round (`launches_before_timed_region`).
+    # r03): W warm-up + K timed steps.  Informational (`cold_start`, --full): round-over-round comparisons must use like for like.  Every
+    # world size runs it (rank 0 reports its own), and its launches COUNT as prewarm launches, so that the number of launches in front of
+    # the timed region is the same for every N, every round and with or without --full (`launches_before_timed_region`).
     cold = None
     launched = 0
-    if a.prewarm >= a.warmup + a.steps:
+    if a.full and a.prewarm >= a.warmup + a.steps:
         for _ in range(a.warmup):
             step()
         torch.cuda.synchronize()
@@ -296,13 +350,14 @@ def main():
                                       "tile_order": kernel_timed.rsplit("order=", 1)[-1] if "order=" in kernel_timed else None,
                                       "start_after_first_us": window["start_after_first_us"],
                                       "end_before_last_us": window["end_before_last_us"]})
+    dumped = dump_outputs(a.dump_outputs, out, rank, world) if a.dump_outputs else None
 
-    # other storage dtypes of the same workload, same run (informational; `value` above is the --io default).
+    # other storage dtypes of the same workload, same run (informational, --full; `value` above is the --io default).
     # BASELINE.json configs[2] words the headline shape as "bf16 in / fp32 compute": both readings are reported.
     variants = {}
     ceilings = {}
     VARIANT_WARMUP = 45        # untimed launches per informational variant: the tensor conversions in between let the power state drop (--prewarm)
-    if world == 1:
+    if world == 1 and a.full:
         from fft_amd import copy_probe, time_kernel
         # what a PURE COPY of the same bytes reaches on this device, in this process (C ABI spectre_probe_copy, fft_amd/csrc/copy_probe.hip):
         #   dense_copy   = 256-KiB contiguous chunks, 16 bytes per lane
@@ -462,7 +517,7 @@ def main():
         alg = algorithmic_bytes(B, N, N, D, G, es, es)
         achieved = alg / (kern_ms * 1e-3) / 1e9
         traffic, traffic_source, traffic_live = None, None, None
-        pmc_why = "--no-pmc" if a.no_pmc else ("N > 1" if world != 1 else None)
+        pmc_why = "no --full" if not a.full else "--no-pmc" if a.no_pmc else ("N > 1" if world != 1 else None)
         if pmc_why is None:
             traffic_live, pmc_why = live_traffic(a)               # behind every timed launch of this process
         if traffic_live is not None:
@@ -536,8 +591,10 @@ def main():
                                                 "hipMemcpyDtoD = hipMemcpyAsync; best_copy = the fastest of all forms")
         if variants:
             res["variants"] = variants
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(N, D, G)
+        if dumped is not None:
+            res["outputs_dumped"] = dumped
         print(json.dumps(res), flush=True)
     hung = bool(rdv.fallback_reason and "not proven within" in rdv.fallback_reason)
     if not hung:

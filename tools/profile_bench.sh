@@ -1,13 +1,13 @@
 #!/bin/bash
 # Round-3 evidence in one go (run on the GPU box:  bash tools/profile_bench.sh <tag>):
-#   1) rocprofv3 --kernel-trace --stats of `python bench.py` (the command the driver runs)   -> summary.txt (per-kernel averages)
+#   1) rocprofv3 --kernel-trace --stats of `python bench.py --full` (headline + variants)    -> summary.txt (per-kernel averages)
 #   2) separate --pmc passes (counters only) of the same command: FETCH_SIZE / WRITE_SIZE     -> profiles/pmc_latest.json via collect_pmc.py
 #   3) L2 <-> memory request mix of the headline kernel (TCC_EA0_*, write-backs)
 set -u
 TAG=${1:-r05}
 REPO=$(pwd); OUT=$REPO/gpurun_out/prof_$TAG; mkdir -p $OUT/summary
 cd /tmp && export TMPDIR=/tmp
-RUN="python $REPO/bench.py --no-cpu-baseline"
+RUN="python $REPO/bench.py --full --no-cpu-baseline"
 timeout 600 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace -o b -- $RUN > $OUT/trace.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 600 rocprofv3 --output-format csv --pmc $c -d $OUT/pmc_$c -o pmc -- $RUN > $OUT/pmc_$c.log 2>&1
